@@ -27,7 +27,11 @@ def _build(tmp_path, example, name):
 
 @pytest.fixture(scope='module')
 def subgraph_lib(tmp_path_factory):
-    so = _build(tmp_path_factory.mktemp('ext'), 'lib_subgraph', 'subgraph_lib')
+    # the library that build() compiled from a reference checkout (oracle/build_ref.py), else built here
+    so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'oracle', '_ref',
+                      'libsubgraph_lib.so')
+    if not os.path.exists(so):
+        so = _build(tmp_path_factory.mktemp('ext'), 'lib_subgraph', 'subgraph_lib')
     mx.library.load(so, verbose=False)
     return so
 

@@ -452,3 +452,59 @@ def test_bench_eight_ranks_through_torchrun():
     rec = json.loads(lines[0])
     assert rec['n_gpus'] == 8 and rec['config']['parallelism'] == 'dp8' and rec['config']['global_batch'] == 16
     assert rec['value'] > 0
+
+
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step computed as float32 .npy files;
+    two runs with the same arguments start from the same seeded inputs and write identical arrays.
+    `--steps` sets the number of timed steps and the result line carries `ms_per_step`."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    env['CUDA_VISIBLE_DEVICES'] = env['HIP_VISIBLE_DEVICES'] = ''      # the CPU path: bit-reproducible
+    dumps = []
+    for d in ('a', 'b'):
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2',
+                              '--warmup', '1', '--batch', '2', '--image-size', '32', '--dtype', 'float32',
+                              '--model', 'resnet18_v1b', '--dump-outputs', str(tmp_path / d)],
+                             capture_output=True, text=True, timeout=300, env=env, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, out.stdout
+        rec = json.loads(lines[0])
+        assert rec['steps'] == 2 and rec['ms_per_step'] > 0
+        assert abs(rec['value'] - 2 * 1000.0 / rec['ms_per_step']) <= 0.01 * rec['value']   # batch 2 per step
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ['loss.npy', 'params_sample.npy']
+        dumps.append({f: np.load(tmp_path / d / f) for f in files})
+    for f, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all()
+        np.testing.assert_array_equal(a, dumps[1][f])
+    assert dumps[0]['loss.npy'].shape == (2,)
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+
+
+def test_bench_algo_table_is_wellformed():
+    """The kernel-selection table a plain `bench.py` run reads: JSON {repr(shape key): candidate name},
+    keys as `kernel_fns._select` looks them up (the repr of a tuple that starts with the pass name)."""
+    import ast
+    import importlib.util
+    import json
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('_bench_for_test', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert os.path.dirname(bench.ALGO_TABLE).startswith(root) and os.path.exists(bench.ALGO_TABLE)
+    with open(bench.ALGO_TABLE) as f:
+        table = json.load(f)
+    assert len(table) >= 100                      # ResNet-50: 20 distinct conv shapes x 3 passes + the FC layer, twice
+    for k, v in table.items():
+        key = ast.literal_eval(re.sub(r'torch\.(float16|bfloat16|float32)', r"'\1'", k))
+        assert isinstance(key, tuple) and isinstance(key[0], str) and repr(key).replace("'float16'", 'torch.float16') == k
+        assert isinstance(v, str) and v
+    # both sets of choices: the default ones and those of deterministic mode (a --dump-outputs run)
+    det = [k for k in table if k.endswith(", 'det')")]
+    assert len(det) >= 50 and len(table) - len(det) >= 50
