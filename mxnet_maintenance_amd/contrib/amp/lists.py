@@ -35,7 +35,8 @@ WIDEST = ['elemwise_add', 'elemwise_sub', 'elemwise_mul', 'elemwise_div', '_plus
           'broadcast_mod', 'broadcast_maximum', 'broadcast_minimum', 'broadcast_hypot', 'broadcast_equal',
           'broadcast_not_equal', 'broadcast_greater', 'broadcast_greater_equal', 'broadcast_lesser',
           'broadcast_lesser_equal', 'Concat', 'concat', 'stack', 'add_n', 'ElementWiseSum', 'where',
-          '_contrib_BatchNormAddReLU', 'BatchNormAddReLU']
+          '_contrib_BatchNormAddReLU', 'BatchNormAddReLU',
+          '_contrib_BatchNormBatchNormAddReLU', 'BatchNormBatchNormAddReLU']
 
 CONDITIONAL_FP32 = [('Activation', 'act_type', ['softrelu']), ('LeakyReLU', 'act_type', ['elu', 'selu'])]
 

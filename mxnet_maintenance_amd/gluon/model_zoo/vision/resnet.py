@@ -9,11 +9,14 @@ MI355X options (not in the reference signature, defaults keep its behaviour):
 weights, BatchNorm over the last axis, NHWC pooling) which is the layout the
 gfx950 conv/BN kernels are written for; ``fuse=True`` folds every BN+ReLU into
 one ``BatchNormWithReLU`` and every bottleneck tail ``relu(BN(x) + shortcut)``
-into one ``BatchNormAddReLU`` kernel.
+into one ``BatchNormAddReLU`` kernel; with both, a projection shortcut's BatchNorm
+is applied by the tail as well (``BatchNormBatchNormAddReLU``).
 """
 from ... import nn
 from ...block import HybridBlock
 from ...nn.basic_layers import _BatchNorm
+from ...parameter import DeferredInitializationError
+from .... import symbol as _symbol
 from ....context import cpu
 
 __all__ = ['ResNetV1', 'ResNetV2', 'BasicBlockV1', 'BasicBlockV2', 'BottleneckV1', 'BottleneckV2',
@@ -67,11 +70,35 @@ class _ResidualTail(_BatchNorm):
     def __init__(self, layout, fuse, **kwargs):
         super().__init__(axis=_bn_axis(layout), **kwargs)
         self._fuse_add = fuse
+        self._shortcut_bn_params = None
 
     def _alias(self):
         return 'batchnorm'
 
+    def fold_shortcut_bn(self, bn):
+        """Let this tail normalise a projection shortcut itself (``BatchNormBatchNormAddReLU``): the
+        block then passes the projection convolution's output as ``shortcut``. ``bn`` stays the owner
+        of its parameters (names, save / load and export are unchanged); only their values are read."""
+        assert bn._kwargs == self._kwargs
+        self._shortcut_bn_params = [bn.gamma, bn.beta, bn.running_mean, bn.running_var]
+
+    def _shortcut_bn_values(self, F, shortcut):
+        if F is _symbol:
+            return [p.var() for p in self._shortcut_bn_params]
+        ctx = shortcut.context
+        try:
+            return [p.data(ctx) for p in self._shortcut_bn_params]
+        except DeferredInitializationError:
+            for p in self._shortcut_bn_params:
+                p.shape = (shortcut.shape[self._kwargs['axis']],)
+                p._finish_deferred_init()
+            return [p.data(ctx) for p in self._shortcut_bn_params]
+
     def hybrid_forward(self, F, x, shortcut, gamma, beta, running_mean, running_var):
+        if self._fuse_add and self._shortcut_bn_params is not None:
+            sg, sb, sm, sv = self._shortcut_bn_values(F, shortcut)
+            return F.contrib.BatchNormBatchNormAddReLU(x, shortcut, gamma, beta, sg, sb, running_mean, running_var,
+                                                       sm, sv, name='fwd', **self._kwargs)
         if self._fuse_add:
             return F.contrib.BatchNormAddReLU(x, shortcut, gamma, beta, running_mean, running_var, name='fwd',
                                               **self._kwargs)
@@ -81,6 +108,20 @@ class _ResidualTail(_BatchNorm):
 def _finish(F, tail, out, shortcut):
     y = tail(out, shortcut)
     return y if tail._fuse_add else F.Activation(y + shortcut, act_type='relu')
+
+
+def _fold_projection_bn(block, layout, fuse):
+    """Fused NHWC blocks with a projection shortcut: its BatchNorm is folded into the residual tail."""
+    block._fold_ds = block.downsample is not None and fuse and layout == 'NHWC'
+    if block._fold_ds:
+        block.tail.fold_shortcut_bn(block.downsample[1])
+
+
+def _shortcut(block, x):
+    if block.downsample is None:
+        return x
+    # folded: the convolution alone, the tail applies the projection's BatchNorm
+    return block.downsample[0](x) if block._fold_ds else block.downsample(x)
 
 
 class BasicBlockV1(HybridBlock):
@@ -99,9 +140,10 @@ class BasicBlockV1(HybridBlock):
         if downsample:
             self.downsample = nn.HybridSequential(prefix='')
             self.downsample.add(_conv(channels, 1, stride, 0, in_channels, layout), _bn(layout))
+        _fold_projection_bn(self, layout, fuse)
 
     def hybrid_forward(self, F, x):
-        shortcut = self.downsample(x) if self.downsample is not None else x
+        shortcut = _shortcut(self, x)
         return _finish(F, self.tail, self.body(x), shortcut)
 
 
@@ -126,6 +168,7 @@ class BottleneckV1(HybridBlock):
         if downsample:
             self.downsample = nn.HybridSequential(prefix='')
             self.downsample.add(_conv(channels, 1, stride, 0, in_channels, layout), _bn(layout))
+        _fold_projection_bn(self, layout, fuse)
         # channel-last 1x1/stride-1 first conv: that conv also emits x for the shortcut branch, so
         # the shortcut's gradient (identity: the tail's d_addend; projection: the downsample conv's
         # dgrad) is folded into this conv's dgrad GEMM (ConvolutionTee, beta = 1) instead of autograd
@@ -140,9 +183,8 @@ class BottleneckV1(HybridBlock):
             out, passthrough = blocks[0](x)
             for b in blocks[1:]:
                 out = b(out)
-            shortcut = self.downsample(passthrough) if self.downsample is not None else passthrough
-            return _finish(F, self.tail, out, shortcut)
-        shortcut = self.downsample(x) if self.downsample is not None else x
+            return _finish(F, self.tail, out, _shortcut(self, passthrough))
+        shortcut = _shortcut(self, x)
         return _finish(F, self.tail, self.body(x), shortcut)
 
 

@@ -227,6 +227,28 @@ def batch_norm(data, gamma, beta, moving_mean, moving_var, eps, momentum, fix_ga
     return out, mean_out, var_out
 
 
+def batch_norm_dual_add_relu(data, shortcut_data, gamma, beta, shortcut_gamma, shortcut_beta, moving_mean,
+                             moving_var, shortcut_moving_mean, shortcut_moving_var, eps, momentum, fix_gamma,
+                             training, axis):
+    """relu(BatchNorm(data) + BatchNorm_shortcut(shortcut_data)) -- a residual tail behind a projection
+    shortcut; returns (out, mean, var) of the main BatchNorm.  On channel-last HIP tensors the shortcut
+    BatchNorm only computes its statistics and the tail's apply pass normalises ``shortcut_data`` itself
+    (kernel_fns.BatchNormDualTailNHWC); otherwise the two operators are composed."""
+    nd = data.dim()
+    if (axis % nd == nd - 1 and nd > 2 and _use_hip(data) and _K.bn_ok(data) and _K.bn_ok(shortcut_data)
+            and shortcut_data.shape == data.shape and shortcut_data.dtype == data.dtype
+            and shortcut_data.device == data.device):
+        g = torch.ones_like(gamma) if fix_gamma else gamma
+        sg = torch.ones_like(shortcut_gamma) if fix_gamma else shortcut_gamma
+        return _K.BatchNormDualTailNHWC.apply(data, shortcut_data, g, beta, sg, shortcut_beta, eps, training,
+                                              moving_mean, moving_var, shortcut_moving_mean, shortcut_moving_var,
+                                              momentum)
+    sc = batch_norm(shortcut_data, shortcut_gamma, shortcut_beta, shortcut_moving_mean, shortcut_moving_var, eps,
+                    momentum, fix_gamma, training, axis, None)[0]
+    return batch_norm(data, gamma, beta, moving_mean, moving_var, eps, momentum, fix_gamma, training, axis, 'relu',
+                      addend=sc)
+
+
 # ---------------------------------------------------------------------------
 # Pooling
 # ---------------------------------------------------------------------------

@@ -13,7 +13,7 @@ from . import kernels as _K
 from .. import _state
 from ..utils import env as _env
 
-__all__ = ['BatchNormNHWC', 'SoftmaxCE', 'GlobalAvgPoolNHWC', 'flat_sgd']
+__all__ = ['BatchNormNHWC', 'BatchNormDualTailNHWC', 'SoftmaxCE', 'GlobalAvgPoolNHWC', 'flat_sgd']
 
 _DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
@@ -97,6 +97,51 @@ class _BnToken:
         self.lazy = None
 
 
+def _bn_fwd_stats(lib, x, gamma, beta, moving_mean, moving_var, eps, training, momentum):
+    """Buffers and launch arguments of one BatchNorm's forward statistics: the batch statistics from the
+    producing conv's epilogue partials or from a reduction of x (training), else the moving statistics.
+    Returns (g, mean, invstd, var, scale, shift, args, host_update): args(relu) is the (gamma, ..., stream)
+    slice of lib.bn_nhwc_forward's arguments; host_update, where not None, updates the moving statistics
+    after the launch (buffers the finalize kernel cannot update in place)."""
+    C = x.shape[-1]
+    R = x.numel() // C
+    dev = x.device
+    g, b, mm = _f32(gamma), _f32(beta), _f32(moving_mean)
+    ext_nblk, center, part = 0, mm, None
+    if training:
+        ext = getattr(x, '_mxamd_bn_part', None)
+        if ext is not None and ext[0].numel() == 2 * C * ext[1] and ext[0].device == dev:
+            # per-channel sum / sum-of-squares partials written by the producing conv's epilogue
+            part, ext_nblk = ext
+            center = _zeros_f32(C, dev)
+        else:
+            part = torch.empty(2 * lib.bn_partials_rows(R, C) * C, dtype=torch.float32, device=dev)
+        mean, invstd, var, scale, shift = torch.empty(5, C, dtype=torch.float32, device=dev).unbind(0)
+    else:
+        mean, var = mm, _f32(moving_var)
+        invstd = torch.rsqrt(var + eps)
+        scale = g * invstd
+        shift = b - mean * scale
+    # moving statistics are updated inside the finalize kernel when the
+    # buffers are fp32 + contiguous (always true for Gluon BN params)
+    upd = (training and momentum is not None and mm is moving_mean and moving_var.dtype == torch.float32
+           and moving_var.is_contiguous())
+
+    def args(relu):
+        return (g.data_ptr(), b.data_ptr(), center.data_ptr(), _p(part), mean.data_ptr(), invstd.data_ptr(),
+                var.data_ptr(), scale.data_ptr(), shift.data_ptr(), R, C, float(eps), int(bool(training)), int(bool(relu)),
+                0, float(momentum or 0.0), moving_mean.data_ptr() if upd else 0, moving_var.data_ptr() if upd else 0,
+                int(ext_nblk), _stream())
+    if training and momentum is not None and not upd:
+        def host_update():
+            with torch.no_grad():
+                moving_mean.mul_(momentum).add_(mean.to(moving_mean.dtype), alpha=1 - momentum)
+                moving_var.mul_(momentum).add_(var.to(moving_var.dtype), alpha=1 - momentum)
+    else:
+        host_update = None
+    return g, mean, invstd, var, scale, shift, args, host_update
+
+
 class BatchNormNHWC(torch.autograd.Function):
     """BatchNorm over the last (channel) axis with optional fused residual add + ReLU."""
 
@@ -110,52 +155,20 @@ class BatchNormNHWC(torch.autograd.Function):
         C = x.shape[-1]
         R = x.numel() // C
         dev = x.device
-        g = _f32(gamma)
-        b = _f32(beta)
-        mm = _f32(moving_mean)
         assert pool is None or (relu and addend is None)
         y = torch.empty_like(x) if pool is None else None
         if addend is not None:
             assert addend.shape == x.shape and addend.dtype == x.dtype
             addend = addend.contiguous()
-        ext_nblk = 0
-        center = mm
-        if training:
-            ext = getattr(x, '_mxamd_bn_part', None)
-            if ext is not None and ext[0].numel() == 2 * C * ext[1] and ext[0].device == dev:
-                # per-channel sum / sum-of-squares partials written by the producing conv's epilogue
-                part, ext_nblk = ext
-                center = _zeros_f32(C, dev)
-            else:
-                nblk = lib.bn_partials_rows(R, C)
-                part = torch.empty(2 * nblk * C, dtype=torch.float32, device=dev)
-            stats = torch.empty(5, C, dtype=torch.float32, device=dev)
-            mean, invstd, var, scale, shift = stats.unbind(0)
-        else:
-            part = None
-            mean = mm
-            invstd = torch.rsqrt(_f32(moving_var) + eps)
-            var = _f32(moving_var)
-            scale = g * invstd
-            shift = b - mean * scale
-        # moving statistics are updated inside the finalize kernel when the
-        # buffers are fp32 + contiguous (always true for Gluon BN params)
-        upd = (training and momentum is not None and mm is moving_mean and moving_var.dtype == torch.float32
-               and moving_var.is_contiguous())
+        g, mean, invstd, var, scale, shift, args, host_update = _bn_fwd_stats(
+            lib, x, gamma, beta, moving_mean, moving_var, eps, training, momentum)
         # residual tail (add + relu): the forward writes a 1-bit-per-element ReLU mask so the backward
         # never re-reads y (two full-tensor reads fewer per call)
         mask = (torch.empty(x.numel() // 8, dtype=torch.uint8, device=dev)
                 if (addend is not None and relu and _RELU_FROM_X[0]) else None)
-        lib.bn_nhwc_forward(_DT[x.dtype], x.data_ptr(), _p(addend), _p(y), _p(mask), g.data_ptr(),
-                            b.data_ptr(),
-                            center.data_ptr(), _p(part), mean.data_ptr(), invstd.data_ptr(), var.data_ptr(),
-                            scale.data_ptr(), shift.data_ptr(), R, C, float(eps), int(bool(training)),
-                            int(bool(relu)), 0, float(momentum or 0.0), moving_mean.data_ptr() if upd else 0,
-                            moving_var.data_ptr() if upd else 0, int(ext_nblk), _stream())
-        if training and momentum is not None and not upd:
-            with torch.no_grad():
-                moving_mean.mul_(momentum).add_(mean.to(moving_mean.dtype), alpha=1 - momentum)
-                moving_var.mul_(momentum).add_(var.to(moving_var.dtype), alpha=1 - momentum)
+        lib.bn_nhwc_forward(_DT[x.dtype], x.data_ptr(), _p(addend), _p(y), _p(mask), *args(relu))
+        if host_update is not None:
+            host_update()
         ctx.pool = None
         if pool is not None:
             (kh, kw), (sh, sw), (ph, pw) = pool
@@ -314,6 +327,114 @@ class BatchNormNHWC(torch.autograd.Function):
             dgamma = out[0].to(gdt) if need_g else None
             dbeta = out[1].to(bdt) if need_b else None
         return dx, dgamma, dbeta, dz, None, None, None, None, None, None, None, None
+
+
+_DUAL_TAIL_USED = [0]    # residual tails that normalised their projection shortcut themselves (tests)
+
+
+def _bn_param_grad_dst(gamma_ref, beta_ref, need_g, need_b, out, C, dev):
+    """Where a BatchNorm backward writes dgamma / dbeta: straight into the parameters' fp32 grad buffers
+    (accumulating) when both are reachable, else into ``out[0:2]``.  Returns (dg_ptr, db_ptr, accum,
+    direct, keep-alive)."""
+    tg = _leaf_grad(gamma_ref, C) if need_g else None
+    tb = _leaf_grad(beta_ref, C) if need_b else None
+    if tb is not None and (tg is not None or not need_g):
+        dg_buf = tg if tg is not None else torch.zeros(C, dtype=torch.float32, device=dev)
+        return dg_buf.data_ptr(), tb.data_ptr(), 1, True, dg_buf
+    return out[0].data_ptr(), out[1].data_ptr(), 0, False, None
+
+
+class BatchNormDualTailNHWC(torch.autograd.Function):
+    """relu(BN(x) + BN_s(z)) over the last axis: a residual tail whose shortcut is a projection's
+    BatchNorm.  The shortcut BatchNorm only produces its statistics and coefficients; the tail's apply
+    pass reads z and normalises it on the fly (rounded to the tensor type as a stored BN_s(z) would be:
+    the result equals BatchNorm followed by BatchNormAddReLU bit for bit), so BN_s(z) is never written
+    or re-read.  One autograd
+    node for both BatchNorms: the backward is the tail's (dx, with the shortcut statistics riding along)
+    followed by the shortcut's apply from dy and the tail's ReLU mask, with no d_addend in between."""
+
+    @staticmethod
+    def forward(ctx, x, z, gamma, beta, zgamma, zbeta, eps, training, moving_mean, moving_var, zmoving_mean,
+                zmoving_var, momentum=None):
+        lib = _K.lib()
+        assert z.shape == x.shape and z.dtype == x.dtype and z.is_contiguous()
+        dev = x.device
+        dt = _DT[x.dtype]
+        zg, zmean, zinvstd, _zvar, zscale, zshift, zargs, zhost = _bn_fwd_stats(
+            lib, z, zgamma, zbeta, zmoving_mean, zmoving_var, eps, training, momentum)
+        if training:
+            # statistics, coefficients and moving-statistics update of the shortcut; no apply (y = null)
+            lib.bn_nhwc_forward(dt, z.data_ptr(), 0, 0, 0, *zargs(False))
+        g, mean, invstd, var, scale, shift, args, host = _bn_fwd_stats(
+            lib, x, gamma, beta, moving_mean, moving_var, eps, training, momentum)
+        y = torch.empty_like(x)
+        mask = torch.empty(x.numel() // 8, dtype=torch.uint8, device=dev)
+        lib.bn_nhwc_forward(dt, x.data_ptr(), z.data_ptr(), y.data_ptr(), mask.data_ptr(), *args(True),
+                            zscale.data_ptr(), zshift.data_ptr())
+        for h in (zhost, host):
+            if h is not None:
+                h()
+        _DUAL_TAIL_USED[0] += 1
+        ctx.save_for_backward(x, z, mask, g, mean, invstd, zg, zmean, zinvstd)
+        ctx.cfg = (bool(training), gamma.dtype, beta.dtype, zgamma.dtype, zbeta.dtype)
+        ctx.refs = (gamma, beta, zgamma, zbeta)
+        ctx.bn_token = None
+        if training and _BN_BWD_FUSE[0]:
+            # the next block's tee dgrad may emit the main BN's backward statistics (as for BatchNormNHWC)
+            ctx.bn_token = _BnToken()
+            y._mxamd_bn_src = (x, mean, None, None, mask, 3, ctx.bn_token)
+        ctx.mark_non_differentiable(mean, var)
+        ctx.set_materialize_grads(False)
+        return y, mean, var
+
+    @staticmethod
+    def backward(ctx, gy, _gm, _gv):
+        lib = _K.lib()
+        x, z, mask, g, mean, invstd, zg, zmean, zinvstd = ctx.saved_tensors
+        training, gdt, bdt, zgdt, zbdt = ctx.cfg
+        gamma_ref, beta_ref, zgamma_ref, zbeta_ref = ctx.refs
+        if gy is None:
+            return (None,) * 13
+        gy = gy.contiguous()
+        C = x.shape[-1]
+        R = x.numel() // C
+        dev = x.device
+        dt = _DT[x.dtype]
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x)
+        dzs = torch.empty_like(z)
+        ext = getattr(gy, '_mxamd_bn_bwd', None)
+        ext_nblk = 0
+        if ext is not None and ctx.bn_token is not None and ext[2] is ctx.bn_token and ext[3] == gy._version:
+            part, ext_nblk = ext[0], ext[1]      # statistics from the producing dgrad's epilogue
+        else:
+            part = torch.empty(2 * lib.bn_partials_rows(R, C) * C, dtype=torch.float32, device=dev)
+        out = torch.empty(5, C, dtype=torch.float32, device=dev)
+        zout = torch.empty(5, C, dtype=torch.float32, device=dev)
+        dg_ptr, db_ptr, accum, direct, _k1 = _bn_param_grad_dst(gamma_ref, beta_ref, need[2], need[3], out, C, dev)
+        zdg_ptr, zdb_ptr, zaccum, zdirect, _k2 = _bn_param_grad_dst(zgamma_ref, zbeta_ref, need[4], need[5], zout, C,
+                                                                    dev)
+        # the tail: finalize + dx; in training mode the same pass reduces the shortcut's statistics
+        ride = training and _BN_TAIL_DS[0]
+        dkw, zpart, znblk = {}, None, 0
+        if ride:
+            znblk = lib.bn_tail_ds_rows(R, C)
+            zpart = torch.empty(2 * znblk * C, dtype=torch.float32, device=dev)
+            dkw = dict(ds_z=z.data_ptr(), ds_mean=zmean.data_ptr(), ds_part=zpart.data_ptr())
+        else:
+            zpart = torch.empty(2 * lib.bn_partials_rows(R, C) * C, dtype=torch.float32, device=dev)
+        lib.bn_nhwc_backward(dt, x.data_ptr(), gy.data_ptr(), 0, mask.data_ptr(), dx.data_ptr(), 0, g.data_ptr(),
+                             mean.data_ptr(), invstd.data_ptr(), 0, 0, part.data_ptr(), dg_ptr, db_ptr,
+                             out[2].data_ptr(), R, C, 3, 0, int(training), accum, _stream(), ext_nblk, **dkw)
+        # the shortcut: finalize + its input's gradient from dy and the tail's mask
+        lib.bn_nhwc_backward(dt, z.data_ptr(), gy.data_ptr(), 0, mask.data_ptr(), dzs.data_ptr(), 0, zg.data_ptr(),
+                             zmean.data_ptr(), zinvstd.data_ptr(), 0, 0, zpart.data_ptr(), zdg_ptr, zdb_ptr,
+                             zout[2].data_ptr(), R, C, 3, 0, int(training), zaccum, _stream(), znblk)
+        dgamma = None if direct or not need[2] else out[0].to(gdt)
+        dbeta = None if direct or not need[3] else out[1].to(bdt)
+        zdgamma = None if zdirect or not need[4] else zout[0].to(zgdt)
+        zdbeta = None if zdirect or not need[5] else zout[1].to(zbdt)
+        return dx, dzs, dgamma, dbeta, zdgamma, zdbeta, None, None, None, None, None, None, None
 
 
 def bnrelu_pool_ok(x, kernel, stride, pad):

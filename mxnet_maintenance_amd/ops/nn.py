@@ -289,6 +289,33 @@ def batch_norm_add_relu(data, addend, gamma, beta, moving_mean, moving_var, eps=
                               training, axis, 'relu', addend=addend)
 
 
+def _bn_dual_infer(in_shapes, a):
+    d = in_shapes[0]
+    if d is None:
+        return {}
+    c = d[a.get('axis', 1) % len(d)]
+    return {i: (c,) for i in range(2, 10)}
+
+
+@register('_contrib_BatchNormBatchNormAddReLU', aliases=('BatchNormBatchNormAddReLU',),
+          arg_names=('data', 'shortcut_data', 'gamma', 'beta', 'shortcut_gamma', 'shortcut_beta'),
+          aux_names=('moving_mean', 'moving_var', 'shortcut_moving_mean', 'shortcut_moving_var'),
+          num_outputs=3, num_visible_outputs=_bn_nvis, infer_params=_bn_dual_infer, params=_BN_PARAMS)
+def batch_norm_batch_norm_add_relu(data, shortcut_data, gamma, beta, shortcut_gamma, shortcut_beta, moving_mean,
+                                   moving_var, shortcut_moving_mean, shortcut_moving_var, eps=1e-3, momentum=0.9,
+                                   fix_gamma=True, use_global_stats=False, output_mean_var=False, axis=1,
+                                   cudnn_off=False, act_type=None, min_calib_range=None, max_calib_range=None):
+    """Fused ``relu(BN(data) + BN_shortcut(shortcut_data))``: the tail of a residual block whose shortcut is a
+    projection (convolution + BatchNorm). ``shortcut_data`` is the projection convolution's output; the two
+    BatchNorms share eps / momentum / fix_gamma / axis. The normalised shortcut is never materialised, and
+    the backward writes no shortcut-sized intermediate gradient either. Extra outputs are the main
+    BatchNorm's."""
+    training = _state.STATE.training and not use_global_stats
+    return hip_ops.batch_norm_dual_add_relu(data, shortcut_data, gamma, beta, shortcut_gamma, shortcut_beta,
+                                            moving_mean, moving_var, shortcut_moving_mean, shortcut_moving_var,
+                                            eps, momentum, fix_gamma, training, axis)
+
+
 # ---------------------------------------------------------------------------
 # Pooling
 # ---------------------------------------------------------------------------

@@ -20,7 +20,8 @@ void bn_nhwc_forward(int dtype, const void* x, const void* addend, void* y, uint
                      const float* beta,
                      const float* center, float* part, float* mean, float* invstd, float* var, float* scale,
                      float* shift, int64_t R, int C, float eps, int training, int relu, int fix_gamma,
-                     float momentum, float* mm_upd, float* mv_upd, int ext_nblk, hipStream_t s);
+                     float momentum, float* mm_upd, float* mv_upd, int ext_nblk, hipStream_t s, const float* ascale,
+                     const float* ashift);
 void bn_nhwc_backward(int dtype, const void* x, const void* dy, const void* y, const uint8_t* mask, void* dx,
                       void* dz,
                       const float* gamma, const float* mean, const float* invstd, const float* fscale,
@@ -437,12 +438,17 @@ PYBIND11_MODULE(_hip_kernels, m) {
                               uintptr_t center, uintptr_t part, uintptr_t mean, uintptr_t inv, uintptr_t var,
                               uintptr_t scale, uintptr_t shift, int64_t R, int C, float eps, int training, int relu,
                               int fix_gamma, float momentum, uintptr_t mm_upd, uintptr_t mv_upd, int ext_nblk,
-                              uintptr_t s) {
+                              uintptr_t s, uintptr_t ascale, uintptr_t ashift) {
     bn_nhwc_forward(dt, P<void>(x), P<void>(add), P<void>(y), P<uint8_t>(mask), P<float>(g), P<float>(b), P<float>(center),
                     P<float>(part), P<float>(mean), P<float>(inv), P<float>(var), P<float>(scale), P<float>(shift), R,
-                    C, eps, training, relu, fix_gamma, momentum, P<float>(mm_upd), P<float>(mv_upd), ext_nblk, S(s));
+                    C, eps, training, relu, fix_gamma, momentum, P<float>(mm_upd), P<float>(mv_upd), ext_nblk, S(s),
+                    P<const float>(ascale), P<const float>(ashift));
     check_launch("bn_nhwc_forward");
-  });
+  }, py::arg("dt"), py::arg("x"), py::arg("add"), py::arg("y"), py::arg("mask"), py::arg("g"), py::arg("b"),
+     py::arg("center"), py::arg("part"), py::arg("mean"), py::arg("inv"), py::arg("var"), py::arg("scale"),
+     py::arg("shift"), py::arg("R"), py::arg("C"), py::arg("eps"), py::arg("training"), py::arg("relu"),
+     py::arg("fix_gamma"), py::arg("momentum"), py::arg("mm_upd"), py::arg("mv_upd"), py::arg("ext_nblk"),
+     py::arg("stream"), py::arg("ascale") = 0, py::arg("ashift") = 0);
   // relu_mode: 0 none, 1 mask from y, 2 mask recomputed from x*fscale+fshift, 3 from the forward's bitmask;
   // accum: += into dgamma/dbeta
   m.def("bn_nhwc_backward", [](int dt, uintptr_t x, uintptr_t dy, uintptr_t y, uintptr_t mask, uintptr_t dx,

@@ -280,20 +280,37 @@ __device__ __forceinline__ void load8f(const float* __restrict__ p, float* o) {
 
 // y = x * scale + shift (+ addend) (relu)
 // MASK: also write the ReLU mask, one byte per 8-element vector (bit i = y[8v+i] > 0)
-template <typename T, bool ADD, bool RELU, bool MASK>
+// AFF (with ADD): the addend is a BatchNorm's input and is normalised here (a projection shortcut's
+// BatchNorm, whose output only this kernel would read): addend * ascale + ashift, rounded to T before the
+// add exactly as the separate apply pass stored it, so the result equals the two-pass one bit for bit
+template <typename T, bool ADD, bool RELU, bool MASK, bool AFF = false>
 __global__ void __launch_bounds__(kBnThreads) bn_apply_kernel(
     const T* __restrict__ x, const T* __restrict__ addend, const float* __restrict__ scale,
-    const float* __restrict__ shift, T* __restrict__ y, uint8_t* __restrict__ mask, int64_t nvec, int C, int nt) {
+    const float* __restrict__ shift, T* __restrict__ y, uint8_t* __restrict__ mask, int64_t nvec, int C, int nt,
+    const float* __restrict__ ascale, const float* __restrict__ ashift) {
+  static_assert(ADD || !AFF, "an affine addend needs the add");
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   int64_t v = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   // channel of this thread's first vector; advancing by `stride` vectors moves
   // the channel by a fixed step (< C), so no per-iteration 64-bit modulo.
   int c = static_cast<int>((v * 8) % C);
   const int cstep = static_cast<int>((stride * 8) % C);
-  float sc[8], sh[8];
-  auto compute = [&](const Vec8<T>& vx, const Vec8<T>& va, int64_t vv) {
+  float sc[8], sh[8], asc[8], ash[8];
+  auto coef = [&](int cc) {
+    load8f(scale + cc, sc);
+    load8f(shift + cc, sh);
+    if (AFF) {
+      load8f(ascale + cc, asc);
+      load8f(ashift + cc, ash);
+    }
+  };
+  auto compute = [&](const Vec8<T>& vx, Vec8<T> va, int64_t vv) {
     Vec8<T> out;
     uint32_t bits = 0;
+    if (AFF) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) va.set(i, va.get(i) * asc[i] + ash[i]);
+    }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       float r = vx.get(i) * sc[i] + sh[i];
@@ -306,8 +323,7 @@ __global__ void __launch_bounds__(kBnThreads) bn_apply_kernel(
     if (MASK) mask[vv] = static_cast<uint8_t>(bits);
   };
   if (cstep == 0) {
-    load8f(scale + c, sc);
-    load8f(shift + c, sh);
+    coef(c);
     for (; v + stride < nvec; v += 2 * stride) {
       Vec8<T> vx0, vx1, va0, va1;
       vload(vx0, x + v * 8, nt);
@@ -331,8 +347,7 @@ __global__ void __launch_bounds__(kBnThreads) bn_apply_kernel(
     Vec8<T> vx, va;
     vload(vx, x + v * 8, nt);
     if (ADD) vload(va, addend + v * 8, nt);
-    load8f(scale + c, sc);
-    load8f(shift + c, sh);
+    coef(c);
     compute(vx, va, v);
   }
 }
@@ -545,7 +560,7 @@ static void bn_forward_impl(const void* x, const void* addend, void* y, uint8_t*
                             const float* beta, const float* center, float* part, float* mean, float* invstd,
                             float* var, float* scale, float* shift, int64_t R, int C, float eps, int training,
                             int relu, int fix_gamma, float momentum, float* mm_upd, float* mv_upd, int ext_nblk,
-                            hipStream_t s) {
+                            hipStream_t s, const float* ascale, const float* ashift) {
   MXAMD_HOST_CHECK(C % 8 == 0, "bn_nhwc: channels must be a multiple of 8");
   BnGeom g = bn_geom(C);
   MXAMD_HOST_CHECK(C % g.cb == 0, "bn_nhwc: unsupported channel count");
@@ -578,11 +593,25 @@ static void bn_forward_impl(const void* x, const void* addend, void* y, uint8_t*
   const T* xa = static_cast<const T*>(x);
   const T* aa = static_cast<const T*>(addend);
   T* ya = static_cast<T*>(y);
+  const float* no_coef = nullptr;
 #define APPLY(ADD, RELU, MASK)                                                                              \
   hipLaunchKernelGGL((bn_apply_kernel<T, ADD, RELU, MASK>), dim3(blocks), dim3(kBnThreads), 0, s, xa, aa, scale, \
-                     shift, ya, mask, nvec, C, bn_nt())
+                     shift, ya, mask, nvec, C, bn_nt(), no_coef, no_coef)
   MXAMD_HOST_CHECK(mask == nullptr || (addend && relu), "bn_nhwc_forward: mask output only for add+relu");
-  if (addend) {
+  MXAMD_HOST_CHECK((ascale == nullptr) == (ashift == nullptr) && (ascale == nullptr || addend),
+                   "bn_nhwc_forward: an affine addend needs the addend and both of its coefficient vectors");
+  if (ascale) {
+    // the addend is a shortcut BatchNorm's input, normalised in this pass
+#define APPLY_AFF(RELU, MASK)                                                                                 \
+  hipLaunchKernelGGL((bn_apply_kernel<T, true, RELU, MASK, true>), dim3(blocks), dim3(kBnThreads), 0, s, xa, aa, \
+                     scale, shift, ya, mask, nvec, C, bn_nt(), ascale, ashift)
+    if (relu) {
+      if (mask) APPLY_AFF(true, true); else APPLY_AFF(true, false);
+    } else {
+      APPLY_AFF(false, false);
+    }
+#undef APPLY_AFF
+  } else if (addend) {
     if (relu) {
       if (mask) APPLY(true, true, true); else APPLY(true, true, false);
     } else {
@@ -798,19 +827,23 @@ void bn_nhwc_forward(int dtype, const void* x, const void* addend, void* y, uint
                      const float* beta,
                      const float* center, float* part, float* mean, float* invstd, float* var, float* scale,
                      float* shift, int64_t R, int C, float eps, int training, int relu, int fix_gamma,
-                     float momentum, float* mm_upd, float* mv_upd, int ext_nblk, hipStream_t s) {
+                     float momentum, float* mm_upd, float* mv_upd, int ext_nblk, hipStream_t s, const float* ascale,
+                     const float* ashift) {
+  // ascale / ashift (null: the addend is added as it is): per-channel coefficients of an addend that is
+  // a BatchNorm's input, see bn_apply_kernel
   switch (dtype) {
     case kF16:
       bn_forward_impl<__half>(x, addend, y, mask, gamma, beta, center, part, mean, invstd, var, scale, shift, R, C, eps,
-                              training, relu, fix_gamma, momentum, mm_upd, mv_upd, ext_nblk, s);
+                              training, relu, fix_gamma, momentum, mm_upd, mv_upd, ext_nblk, s, ascale, ashift);
       break;
     case kBF16:
       bn_forward_impl<__hip_bfloat16>(x, addend, y, mask, gamma, beta, center, part, mean, invstd, var, scale, shift, R,
-                                      C, eps, training, relu, fix_gamma, momentum, mm_upd, mv_upd, ext_nblk, s);
+                                      C, eps, training, relu, fix_gamma, momentum, mm_upd, mv_upd, ext_nblk, s, ascale,
+                                      ashift);
       break;
     default:
       bn_forward_impl<float>(x, addend, y, mask, gamma, beta, center, part, mean, invstd, var, scale, shift, R, C, eps,
-                             training, relu, fix_gamma, momentum, mm_upd, mv_upd, ext_nblk, s);
+                             training, relu, fix_gamma, momentum, mm_upd, mv_upd, ext_nblk, s, ascale, ashift);
   }
 }
 

@@ -604,52 +604,83 @@ __device__ __forceinline__ f4_t load4<__hip_bfloat16>(const __hip_bfloat16* p) {
               __uint_as_float(r.y & 0xffff0000u)};
 }
 
-// Sum `nrows` slab rows (row r at slab + r*row_stride) column-wise, 4 columns per thread.
-// FINAL: out = (accum ? out : 0) + sum (converted to OutT); else the partial sum
-// overwrites row 0 of the group (only this thread ever reads those columns).
-template <typename OutT, bool FINAL>
-__global__ void __launch_bounds__(256) wgrad_reduce_kernel(float* __restrict__ slab, int nrows, int64_t row_stride,
-                                                           int rows_per_group, int64_t n, OutT* __restrict__ out,
-                                                           int accum) {
-  const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i4 >= n) return;
-  const int r0 = blockIdx.y * rows_per_group;
-  const int r1 = min(nrows, r0 + rows_per_group);
-  float* base = slab + i4;
+// Column-wise sum of rows r0 .. r1-1 (row r at base + r*stride), 4 columns: four accumulators take
+// consecutive rows in turn (four loads in flight), the remainder goes to the first, then s0 + ((s1 + s2) + s3).
+// Every reduce below is built from this one order.
+__device__ __forceinline__ f4_t sum_rows4(const float* base, int64_t stride, int r0, int r1) {
   f4_t s0 = f4_t{0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
   int r = r0;
   for (; r + 3 < r1; r += 4) {
-    s0 += *reinterpret_cast<const f4_t*>(base + (int64_t)r * row_stride);
-    s1 += *reinterpret_cast<const f4_t*>(base + (int64_t)(r + 1) * row_stride);
-    s2 += *reinterpret_cast<const f4_t*>(base + (int64_t)(r + 2) * row_stride);
-    s3 += *reinterpret_cast<const f4_t*>(base + (int64_t)(r + 3) * row_stride);
+    s0 += *reinterpret_cast<const f4_t*>(base + (int64_t)r * stride);
+    s1 += *reinterpret_cast<const f4_t*>(base + (int64_t)(r + 1) * stride);
+    s2 += *reinterpret_cast<const f4_t*>(base + (int64_t)(r + 2) * stride);
+    s3 += *reinterpret_cast<const f4_t*>(base + (int64_t)(r + 3) * stride);
   }
-  for (; r < r1; ++r) s0 += *reinterpret_cast<const f4_t*>(base + (int64_t)r * row_stride);
+  for (; r < r1; ++r) s0 += *reinterpret_cast<const f4_t*>(base + (int64_t)r * stride);
   s0 += s1 + s2 + s3;
-  if (FINAL) {
-    if (accum) s0 += load4<OutT>(out + i4);
-    store4<OutT>(out + i4, s0);
-  } else {
-    *reinterpret_cast<f4_t*>(base + (int64_t)r0 * row_stride) = s0;
+  return s0;
+}
+
+// Sum the `nrows` slab rows (row r at slab + r*n) column-wise, 4 columns per thread:
+// out = (accum ? out : 0) + sum (converted to OutT).  The slab is only read.
+template <typename OutT>
+__global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* __restrict__ slab, int nrows, int64_t n,
+                                                           OutT* __restrict__ out, int accum) {
+  const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  f4_t s0 = sum_rows4(slab + i4, n, 0, nrows);
+  if (accum) s0 += load4<OutT>(out + i4);
+  store4<OutT>(out + i4, s0);
+}
+
+// LDS of the lanes kernel: one fp32 quad per (row group, column quad)
+constexpr int kReduceLdsQuads = 2048;
+
+// The same sum for small outputs, where one thread per column quad leaves most of the GPU idle.  The rows
+// are cut into `groups` runs of `rpg` consecutive rows; a workgroup owns `cq` consecutive column quads and
+// its 256 threads are cq quads x 256/cq row lanes.  Lane l sums groups l, l + lanes, ... (sum_rows4 each)
+// into LDS, and lane 0 sums the group results, again with sum_rows4.  These are the additions, in the
+// order, of the earlier two launches (fold each row group, then sum the groups), so results did not change
+// when the launches became one; the order depends on (nrows, n) alone.
+template <typename OutT>
+__global__ void __launch_bounds__(256) wgrad_reduce_lanes_kernel(const float* __restrict__ slab, int nrows, int64_t n,
+                                                                 int groups, int rpg, int cq, OutT* __restrict__ out,
+                                                                 int accum) {
+  __shared__ f4_t red[kReduceLdsQuads];
+  const int lanes = 256 / cq;
+  const int q = threadIdx.x % cq, lane = threadIdx.x / cq;
+  const int64_t i4 = ((int64_t)blockIdx.x * cq + q) * 4;
+  const bool live = i4 < n;
+  if (live) {
+    for (int g = lane; g < groups; g += lanes)
+      red[g * cq + q] = sum_rows4(slab + i4, n, g * rpg, min(nrows, (g + 1) * rpg));
   }
+  __syncthreads();
+  if (lane != 0 || !live) return;
+  f4_t s0 = sum_rows4(reinterpret_cast<const float*>(red + q), (int64_t)cq * 4, 0, groups);
+  if (accum) s0 += load4<OutT>(out + i4);
+  store4<OutT>(out + i4, s0);
 }
 
 template <typename OutT>
 void launch_reduce(float* slab, int splits, int64_t n, OutT* out, int accum, hipStream_t s) {
   // enough threads to stream the slab: split the rows into groups when the output is small
   const int64_t cols4 = n / 4;
-  const unsigned gx = (unsigned)((cols4 + 255) / 256);
   int groups = (int)std::min<int64_t>(splits, std::max<int64_t>(1, (256 * 256 * 2) / std::max<int64_t>(cols4, 1)));
   const int rpg = (splits + groups - 1) / groups;
   groups = (splits + rpg - 1) / rpg;
-  if (groups > 1) {
-    hipLaunchKernelGGL((wgrad_reduce_kernel<OutT, false>), dim3(gx, groups), dim3(256), 0, s, slab, splits, n, rpg, n,
-                       out, accum);
-    hipLaunchKernelGGL((wgrad_reduce_kernel<OutT, true>), dim3(gx, 1), dim3(256), 0, s, slab, groups,
-                       (int64_t)rpg * n, groups, n, out, accum);
+  if (groups > 1 && groups <= kReduceLdsQuads) {
+    // column quads per workgroup: as many as still leave a few hundred workgroups (8 quads = one 128-byte
+    // line per row at the least), no more row lanes than groups, and the group results must fit the LDS
+    int cq = cols4 / 64 >= 512 ? 64 : cols4 / 32 >= 512 ? 32 : cols4 / 16 >= 256 ? 16 : 8;
+    while (cq < 64 && 256 / cq >= 2 * groups) cq *= 2;
+    while (cq > 1 && groups * cq > kReduceLdsQuads) cq /= 2;
+    hipLaunchKernelGGL((wgrad_reduce_lanes_kernel<OutT>), dim3((unsigned)((cols4 + cq - 1) / cq)), dim3(256), 0, s,
+                       slab, splits, n, groups, rpg, cq, out, accum);
   } else {
-    hipLaunchKernelGGL((wgrad_reduce_kernel<OutT, true>), dim3(gx, 1), dim3(256), 0, s, slab, splits, n, splits, n,
-                       out, accum);
+    // large output (or more row groups than the LDS holds, on a tiny one): one thread per column quad
+    hipLaunchKernelGGL((wgrad_reduce_kernel<OutT>), dim3((unsigned)((cols4 + 255) / 256)), dim3(256), 0, s, slab,
+                       splits, n, out, accum);
   }
 }
 
