@@ -190,6 +190,9 @@ class BatchNormNHWC(torch.autograd.Function):
         ctx.cfg = (relu_mode, bool(training), addend is not None, gamma.dtype, beta.dtype)
         # the addend is a tee conv's passthrough: the shortcut gradient may be handed over lazily
         ctx.tee_key = getattr(addend, '_mxamd_tee_key', None) if (addend is not None and relu_mode == 3) else None
+        # x is the output of a 1x1 conv whose backward can form this tail's dx itself (conv_pw_bwd): the
+        # (joint key, token) of that conv call, see ConvNHWC.backward
+        ctx.bwd1x1 = getattr(x, '_mxamd_bwd1x1', None) if (relu_mode == 3 and training) else None
         ctx.bn_token = None
         if training and relu_mode in (0, 2, 3) and _BN_BWD_FUSE[0] and pool is None:
             # a consumer convolution's dgrad (big-tile kernel) may emit this BN's backward statistics
@@ -248,7 +251,6 @@ class BatchNormNHWC(torch.autograd.Function):
                 lazy_mask = mask_l
             else:
                 gy = (gy - dy_l + _materialize_dz(dy_l, mask_l)).contiguous()
-        dx = torch.empty_like(x)
         dz = torch.empty_like(x) if has_add else None
         ext = getattr(gy, '_mxamd_bn_bwd', None)
         ext_nblk = 0
@@ -273,7 +275,8 @@ class BatchNormNHWC(torch.autograd.Function):
             # statistics and dx straight from the pooled gradient (two gather passes, pool_nhwc.hip): the
             # routed full-resolution gradient is never materialised
             N_, H_, W_, C_, Ho_, Wo_, kh, kw, sh, sw, ph, pw, _ = ctx.pool
-            ppart = torch.empty(2 * lib.bn_pool_bwd_blocks() * C, dtype=torch.float32, device=dev)
+            dx = torch.empty_like(x)
+            ppart =torch.empty(2 * lib.bn_pool_bwd_blocks() * C, dtype=torch.float32, device=dev)
             lib.bn_pool_backward(_DT[x.dtype], x.data_ptr(), gy.data_ptr(), y.data_ptr(), dx.data_ptr(), g.data_ptr(),
                                  mean.data_ptr(), invstd.data_ptr(), fscale.data_ptr(), fshift.data_ptr(),
                                  ppart.data_ptr(), dg_ptr, db_ptr, out[2].data_ptr(), N_, H_, W_, C_, Ho_, Wo_, kh, kw,
@@ -302,11 +305,29 @@ class BatchNormNHWC(torch.autograd.Function):
             ds_nblk = lib.bn_tail_ds_rows(R, C)
             ds_part = torch.empty(2 * ds_nblk * C, dtype=torch.float32, device=dev)
             dkw = dict(ds_z=ds[0].data_ptr(), ds_mean=ds[1].data_ptr(), ds_part=ds_part.data_ptr())
-        lib.bn_nhwc_backward(_DT[x.dtype], x.data_ptr(), gy.data_ptr(), _p(y), _p(ymask), dx.data_ptr(), _p(dz),
-                             g.data_ptr(),
+        # x came from a 64 -> 256 1x1 conv whose backward can apply A, B, Cc itself (conv_pw_bwd's prologue):
+        # once that joint algorithm is chosen, only the statistics and coefficients are computed here and gy
+        # goes back as the "gradient" of x with (x, mask, coefficients) on the conv's token; ConvNHWC.backward
+        # checks that it received this very tensor and otherwise materialises dx.  Until then dx is
+        # materialised as usual and the same record lets the conv time both ways.
+        hand = None
+        if (ctx.bwd1x1 is not None and _LAZY_BN_APPLY[0] and relu_mode == 3 and lazy_mask is None and ds is None
+                and training and ymask is not None and gy.data_ptr() % 16 == 0):
+            hand = (ctx.bwd1x1[0] + ('apply', bool(lazy)), ctx.bwd1x1[1])
+        take = hand is not None and _joint_algo(hand[0]) == 'fused'
+        if take and dz is not None:
+            # (no tee data gradient takes the mask lazily here: the shortcut gradient is multiplied out)
+            dz = _materialize_dz(gy, ymask) if ctx.needs_input_grad[3] else None
+        dx = None if take else torch.empty_like(x)
+        lib.bn_nhwc_backward(_DT[x.dtype], x.data_ptr(), gy.data_ptr(), _p(y), _p(ymask), _p(dx),
+                             0 if take else _p(dz), g.data_ptr(),
                              mean.data_ptr(), invstd.data_ptr(), _p(fscale), _p(fshift), part.data_ptr(), dg_ptr,
                              db_ptr, out[2].data_ptr(), R, C, kmode, 0, int(training), accum, _stream(),
                              ext_nblk, **dkw)
+        if hand is not None:
+            carrier = gy if take else dx
+            hand[1].lazy = (carrier, carrier._version, gy, x, ymask, out, hand[0], not take, bool(lazy))
+            dx = carrier
         if ds is not None:
             # consumed by the shortcut BN's backward (token + version checked there)
             if lazy_ds:
@@ -1749,6 +1770,153 @@ def _wgrad_maybe_side(dy, x, w, w_ref, stride, pad):
     return dw
 
 
+# ---------------------------------------------------------------- one-pass backward of the 64 -> 256 1x1 conv
+# src/kernels/conv_pw_bwd.hip computes dX and dW from one read of dY, and can form dY itself from a residual
+# tail's (dy, x3, mask, A, B, Cc).  Whether it replaces the data-gradient + weight-gradient pair is one joint
+# autotuned choice per shape, key ('bwd1x1', x shape, w shape, dtype, mode...): mode 'plain' (dY given) or
+# 'apply' (the tail BatchNorm's apply folded in, BatchNormNHWC.backward).
+_LAZY_BN_APPLY = [True]    # tails may hand their apply pass to the conv behind them (tests flip it)
+_PW_BWD_USED = [0, 0]      # fused launches: [plain, with the BatchNorm prologue] (tests)
+
+
+def _joint_algo(key):
+    """The joint choice recorded for ``key`` (this process's, else the stored tuning table's), or None."""
+    k = _akey(key)
+    name = _ALGO.get(k)
+    if name is None:
+        _load_tuning_file()
+        name = _FILE_ALGO.get(repr(k))
+        if name is not None:
+            _ALGO[k] = name
+    return name
+
+
+def _bwd1x1_base(x, w, stride, pad):
+    """Joint-choice key stem when conv_pw_bwd is built for this conv, else None."""
+    K, R, S, C = w.shape
+    if not (_CONV_HIP and R == 1 and S == 1 and tuple(stride) == (1, 1) and tuple(pad) == (0, 0) and x.is_cuda
+            and x.dtype in (torch.float16, torch.bfloat16) and w.dtype == x.dtype and x.dim() == 4):
+        return None
+    lib = _K.lib()
+    if not (hasattr(lib, 'conv_pw_bwd') and lib.conv_pw_bwd_ok(int(C), int(K))):
+        return None
+    return ('bwd1x1', tuple(x.shape), tuple(w.shape), x.dtype)
+
+
+def pw_bwd_ok(dy, x, w):
+    """True when conv_pw_bwd takes these operands: Cin = 64, Cout = 256, contiguous, 16-byte aligned."""
+    return (_bwd1x1_base(x, w, (1, 1), (0, 0)) is not None and dy.dtype == x.dtype and dy.is_contiguous()
+            and x.is_contiguous() and w.is_contiguous() and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
+            and w.data_ptr() % 16 == 0 and tuple(dy.shape) == tuple(x.shape[:-1]) + (w.shape[0],)
+            and dy.numel() < 2 ** 31)
+
+
+def conv_pw_bwd(dy, x, w, w_ref, apply=None, max_blocks=None, out=None):
+    """(dX, dW) of y = x . w^T (w [256][1][1][64]) from one pass over ``dy``.  dW is accumulated into
+    ``out``, else into the leaf grad buffer of ``w_ref`` as ``_wgrad`` does (None is returned for it then),
+    else returned.  ``apply`` = (x3, mask, coef): ``dy`` is a residual tail's incoming gradient and the
+    gradient actually used is A * (mask bit ? dy : 0) + B * x3 + Cc, coef the tail's [5][256] finalize
+    output (rows 2..4 = A, B, Cc), rounded as the apply kernel stores it.  ``max_blocks``: workgroups
+    (default one per CU), each over one contiguous pixel range: with the split count of the in-tree weight
+    gradients (conv_wgrad.hip; one per CU is the ring kernels' plan here) dW equals theirs bit for bit, as dX
+    equals the streaming data gradient's."""
+    K, C = w.shape[0], w.shape[3]
+    M = dy.numel() // K
+    if not pw_bwd_ok(dy, x, w):
+        raise ValueError('conv_pw_bwd: needs Cin = 64, Cout = 256, contiguous 16-byte aligned f16 / bf16 operands')
+    lib = _K.lib()
+    blocks = int(max_blocks) if max_blocks else _num_cus(dy.device)
+    wt = _dgrad_weight(w)                  # W^T [64][1][1][256]
+    dx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    slab = torch.empty(blocks * K * C, dtype=torch.float32, device=x.device)
+    a = (0, 0, 0, 0, 0)
+    if apply is not None:
+        x3, mask, coef = apply
+        if not (x3.shape == dy.shape and x3.dtype == dy.dtype and x3.is_contiguous() and x3.data_ptr() % 16 == 0
+                and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() * 8 == dy.numel()
+                and coef.dtype == torch.float32 and coef.is_contiguous() and tuple(coef.shape) == (5, K)):
+            raise ValueError('conv_pw_bwd: apply = (x3 like dy, 1-bit mask, fp32 coefficients [5][256])')
+        a = (x3.data_ptr(), mask.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), coef[4].data_ptr())
+    lib.conv_pw_bwd(_DT[dy.dtype], dy.data_ptr(), *a, x.data_ptr(), wt.data_ptr(), dx.data_ptr(), slab.data_ptr(),
+                    M, C, K, blocks, _stream())
+    _PW_BWD_USED[int(apply is not None)] += 1
+    tgt = out if out is not None else _leaf_grad(w_ref, dtype=w.dtype)
+    if tgt is not None:
+        assert tgt.is_contiguous() and tgt.numel() == K * C and tgt.dtype in _DT
+        lib.slab_reduce(_DT[tgt.dtype], slab.data_ptr(), blocks, K * C, tgt.data_ptr(), 1, _stream())
+        return dx, None
+    dw = torch.empty(w.shape, dtype=w.dtype, device=w.device)
+    lib.slab_reduce(_DT[dw.dtype], slab.data_ptr(), blocks, K * C, dw.data_ptr(), 0, _stream())
+    return dx, dw
+
+
+def _bn_dx_torch(x, dy, mask, A, B, Cc):
+    """dx = A * (mask bit ? dy : 0) + B * x + Cc in fp32, rounded to x's dtype: the tail's backward apply."""
+    bits = ((mask.view(-1, 1) >> torch.arange(8, device=mask.device, dtype=torch.uint8)) & 1).view(dy.shape)
+    dz = torch.where(bits.bool(), dy.float(), torch.zeros((), dtype=torch.float32, device=dy.device))
+    return (A * dz + B * x.float() + Cc).to(x.dtype)
+
+
+def _bn_dx(x, dy, mask, coef):
+    """The tail's dx materialised from a hand-over record: the apply kernel alone (coefficients are
+    rows 2..4 of ``coef``), pure torch off the GPU."""
+    if not (x.is_cuda and _K.available() and x.dtype in (torch.float16, torch.bfloat16)):
+        return _bn_dx_torch(x, dy, mask, coef[2], coef[3], coef[4])
+    dx = torch.empty_like(x)
+    C = x.shape[-1]
+    _K.lib().bn_bwd_apply(_DT[x.dtype], x.data_ptr(), dy.data_ptr(), mask.data_ptr(), coef[2].data_ptr(),
+                          dx.data_ptr(), x.numel() // C, C, _stream())
+    return dx
+
+
+def _bwd1x1_tune(jkey, dy, x, w, stride, pad, bn_src, rec):
+    """Time the chosen data-gradient + weight-gradient pair against conv_pw_bwd as whole closures and
+    record the joint choice.  Nothing here touches a real gradient: the pair's weight gradient is the
+    out-of-place candidate and the fused kernel accumulates into a scratch buffer."""
+    fusable = _bn_bwd_fusable(bn_src, x.shape)
+    dkey = ('dgrad', tuple(x.shape), tuple(w.shape), tuple(stride), tuple(pad), x.dtype) + (('bnbwd',) if fusable
+                                                                                             else ())
+    wkey = ('wgrad', tuple(x.shape), tuple(w.shape), tuple(stride), tuple(pad), x.dtype)
+    dg, wg = _ALGO.get(_akey(dkey)), _ALGO.get(_akey(wkey))
+    if dg is None or wg is None:
+        return
+    if fusable:
+        dfn = dict(_dgrad_bn_candidates(dy, x, w, stride, pad, bn_src)[1]).get(dg)
+    else:
+        dfn = dict(_dgrad_candidates(dy, x, w, stride, pad)).get(dg)
+    wfn = dict(_wgrad_candidates(dy, x, w, stride, pad)).get(wg)
+    if dfn is None or wfn is None:
+        return
+    scratch = torch.zeros_like(w)
+    if rec is not None:
+        gy, x3, mask, coef, lazy_dz = rec
+
+        def pair():
+            _bn_dx(x3, gy, mask, coef)          # the apply pass the fused kernel absorbs (dy holds its result)
+            wfn()
+            return dfn()
+
+        def fused():
+            if not lazy_dz:
+                _materialize_dz(gy, mask)       # the shortcut gradient the apply kernel no longer writes
+            return conv_pw_bwd(gy, x, w, None, apply=(x3, mask, coef), out=scratch)[0]
+    else:
+        def pair():
+            wfn()
+            return dfn()
+
+        def fused():
+            return conv_pw_bwd(dy, x, w, None, out=scratch)[0]
+    if fusable:
+        fused = _charge_bn_bwd([('fused', fused)], bn_src[0])[0][1]
+    # the pair is named after its parts, vendor part first: the vendor margin and the determinism filter
+    # then apply to it as to any library candidate
+    pname = '+'.join(sorted([dg, wg], key=lambda n_: not _is_vendor(n_)))
+    used = list(_PW_BWD_USED)
+    _select(jkey, [(pname, pair), ('fused', fused)], pname)
+    _PW_BWD_USED[:] = used
+
+
 class ConvNHWC(torch.autograd.Function):
     """2-D NHWC convolution with per-shape algorithm selection (HIP MFMA kernel / hipBLASLt / MIOpen)."""
 
@@ -1763,6 +1931,12 @@ class ConvNHWC(torch.autograd.Function):
         ctx.b_ref = bias
         ctx.w_ref = w
         ctx.bn_src = getattr(x, '_mxamd_bn_src', None)
+        # 64 -> 256: the backward may run as one kernel; a residual tail consuming y finds the joint key and
+        # this call's token on it and may leave its apply pass to that kernel
+        base = _bwd1x1_base(x, w, stride, pad)
+        ctx.bwd1x1 = None
+        if base is not None:
+            ctx.bwd1x1 = y._mxamd_bwd1x1 = (base, _BnToken())
         return y
 
     @staticmethod
@@ -1771,6 +1945,37 @@ class ConvNHWC(torch.autograd.Function):
         dy = dy.contiguous()
         stride, pad = ctx.stride, ctx.pad
         dx = dw = db = None
+        jkey = rec = None
+        if ctx.bwd1x1 is not None:
+            base, tok = ctx.bwd1x1
+            hand, tok.lazy = tok.lazy, None
+            same = False
+            if hand is not None:
+                carrier, ver, gy_l, x3, mask, coef, akey, materialised, lazy_dz = hand
+                same = dy is carrier and dy._version == ver
+                if not materialised and not (same and _joint_algo(akey) == 'fused' and pw_bwd_ok(dy, x, w)
+                                             and not (ctx.has_bias and ctx.needs_input_grad[2])
+                                             and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
+                                             and not _WGRAD_SIDE[0]):
+                    # the tail returned its dy in place of dx: another gradient was summed in, or this
+                    # backward cannot run the fused kernel after all -- put the real dx in its place
+                    dx3 = _bn_dx(x3, gy_l, mask, coef)
+                    dy = dx3 if same else (dy - gy_l + dx3).contiguous()
+                    same, materialised = False, True
+            if (ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not _WGRAD_SIDE[0]
+                    and pw_bwd_ok(dy, x, w)):
+                if hand is not None and same:
+                    jkey, rec = akey, (gy_l, x3, mask, coef, lazy_dz)
+                else:
+                    jkey = base + ('plain',)
+                if _joint_algo(jkey) == 'fused':
+                    if rec is not None and not materialised:
+                        dx, dw = conv_pw_bwd(gy_l, x, w, ctx.w_ref, apply=(x3, mask, coef))
+                    else:
+                        dx, dw = conv_pw_bwd(dy, x, w, ctx.w_ref)
+                    if ctx.has_bias and ctx.needs_input_grad[2]:
+                        db = _conv_bias_grad(dy, ctx.b_ref)
+                    return dx, dw, db, None, None, None
         if ctx.needs_input_grad[1] and _WGRAD_SIDE[0]:
             # first, so that it overlaps the dgrad and what follows it
             dw = _wgrad_maybe_side(dy, x, w, ctx.w_ref, stride, pad)
@@ -1785,6 +1990,11 @@ class ConvNHWC(torch.autograd.Function):
             dw = _wgrad(dy, x, w, ctx.w_ref, stride, pad)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = _conv_bias_grad(dy, ctx.b_ref)
+        if (jkey is not None and _joint_algo(jkey) is None and _AUTOTUNE
+                and not torch.cuda.is_current_stream_capturing()):
+            # first encounter: the pair above produced this call's gradients; now that its parts are
+            # chosen, time it against the one-pass kernel for the next call
+            _bwd1x1_tune(jkey, dy, x, w, stride, pad, ctx.bn_src, rec)
         return dx, dw, db, None, None, None
 
 

@@ -199,6 +199,12 @@ void conv_pw_stream(int dtype, const void* x, const void* w, void* y, const void
                     const uint8_t* bn_mask, const float* bn_mean, const float* bn_scale, const float* bn_shift,
                     int bn_mode, const uint8_t* addend_mask);
 int conv_pw_stream_bnb_ok(int kin, int nout, int add, int mode);
+void bn_bwd_apply(int dtype, const void* x, const void* dy, const uint8_t* mask, const float* coef, void* dx,
+                  int64_t R, int C, hipStream_t s);
+int conv_pw_bwd_ok(int cin, int cout);
+void conv_pw_bwd(int dtype, const void* dy, const void* x3, const uint8_t* mask, const float* A, const float* B,
+                 const float* Cc, const void* X, const void* wt, void* dX, float* slab, int64_t M, int cin, int cout,
+                 int blocks, hipStream_t s);
 void conv_gen(int dtype, int mode, const void* src, const void* wsrc, const float* bias, void* dst, const int* geom,
               int splits, hipStream_t s);
 void rnn_fwd_seq(int dtype, int mode, const float* gx, const void* h0, const float* c0, const void* whh,
@@ -316,6 +322,24 @@ PYBIND11_MODULE(_hip_kernels, m) {
      pybind11::arg("bn_mask") = 0, pybind11::arg("bn_mean") = 0, pybind11::arg("bn_scale") = 0,
      pybind11::arg("bn_shift") = 0, pybind11::arg("bn_mode") = 0, pybind11::arg("addend_mask") = 0);
   m.def("conv_pw_stream_bnb_ok", &conv_pw_stream_bnb_ok);
+  // one-pass data + weight gradient of the 64 -> 256 1x1 conv (src/kernels/conv_pw_bwd.hip); x3 != 0: with the
+  // residual-tail BatchNorm's backward apply as the prologue
+  // dx = A * (mask bit ? dy : 0) + B * x + Cc from coef[3][C]: a residual tail's backward apply alone
+  m.def("bn_bwd_apply", [](int dt, uintptr_t x, uintptr_t dy, uintptr_t mask, uintptr_t coef, uintptr_t dx, int64_t R,
+                           int C, uintptr_t s) {
+    bn_bwd_apply(dt, P<const void>(x), P<const void>(dy), P<const uint8_t>(mask), P<const float>(coef), P<void>(dx), R,
+                 C, S(s));
+    check_launch("bn_bwd_apply");
+  });
+  m.def("conv_pw_bwd_ok", &conv_pw_bwd_ok);
+  m.def("conv_pw_bwd", [](int dt, uintptr_t dy, uintptr_t x3, uintptr_t mask, uintptr_t A, uintptr_t B, uintptr_t Cc,
+                          uintptr_t X, uintptr_t wt, uintptr_t dX, uintptr_t slab, int64_t M, int cin, int cout,
+                          int blocks, uintptr_t s) {
+    conv_pw_bwd(dt, P<const void>(dy), P<const void>(x3), P<const uint8_t>(mask), P<const float>(A), P<const float>(B),
+                P<const float>(Cc), P<const void>(X), P<const void>(wt), P<void>(dX), P<float>(slab), M, cin, cout,
+                blocks, S(s));
+    check_launch("conv_pw_bwd");
+  });
   // general implicit-GEMM convolution: grouped / dilated / 1-3-D / fp32 / transposed (src/kernels/conv_gen.hip)
   m.def("conv_gen", [](int dt, int mode, uintptr_t src, uintptr_t wsrc, uintptr_t bias, uintptr_t dst,
                        std::vector<int> geom, int splits, uintptr_t s) {

@@ -658,6 +658,12 @@ static void bn_backward_impl(const void* x, const void* dy, const void* y, const
   hipLaunchKernelGGL((bn_finalize_kernel<1>), dim3((C + kFinPerBlock - 1) / kFinPerBlock), dim3(kFinThreads), 0, s, p1, p2, nblk, C, R, mean, gamma, nullptr,
                      invstd, 0.f, dgamma, dbeta, A, B, Cc, nullptr, fix_gamma, training, 0.f, nullptr,
                      nullptr, accum);
+  // dx == nullptr: coefficients only -- the consumer of dx forms it from (dy, x, mask, A, B, Cc) itself
+  // (conv_pw_bwd.hip's prologue)
+  if (dx == nullptr) {
+    MXAMD_HOST_CHECK(dz == nullptr && ds_z == nullptr, "bn_nhwc_backward: coefficients only writes no gradient");
+    return;
+  }
   const int64_t nvec = R * C / 8;
   int blocks = static_cast<int>((nvec + kBnThreads - 1) / kBnThreads);
   if (blocks > 256 * 16) blocks = 256 * 16;
@@ -856,6 +862,25 @@ void bn_finalize_backward(const float* part, int nblk, int C, int64_t R, const f
   hipLaunchKernelGGL((bn_finalize_kernel<1>), dim3((C + kFinPerBlock - 1) / kFinPerBlock), dim3(kFinThreads), 0, s, part,
                      part + static_cast<int64_t>(nblk) * C, nblk, C, R, mean, gamma, nullptr, invstd, 0.f, dgamma,
                      dbeta, coef, coef + C, coef + 2 * C, nullptr, fix_gamma, training, 0.f, nullptr, nullptr, accum);
+}
+
+// The apply pass of a residual tail's backward alone, from coefficients coef[3][C] (A, B, Cc) a
+// coefficients-only bn_nhwc_backward left: dx = A * (mask bit ? dy : 0) + B * x + Cc.
+void bn_bwd_apply(int dtype, const void* x, const void* dy, const uint8_t* mask, const float* coef, void* dx,
+                  int64_t R, int C, hipStream_t s) {
+  MXAMD_HOST_CHECK(C % 8 == 0 && x && dy && mask && coef && dx, "bn_bwd_apply: operands");
+  MXAMD_HOST_CHECK(dtype == kF16 || dtype == kBF16, "bn_bwd_apply: dtype must be f16 or bf16");
+  const int64_t nvec = R * C / 8;
+  int blocks = static_cast<int>((nvec + kBnThreads - 1) / kBnThreads);
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  const float* none = nullptr;
+#define APPLY_ONLY(T)                                                                                              \
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, kReluFromMask, false>), dim3(blocks), dim3(kBnThreads), 0, s,           \
+                     static_cast<const T*>(x), static_cast<const T*>(dy), static_cast<const T*>(nullptr), mask, coef, \
+                     coef + C, coef + 2 * C, none, none, static_cast<T*>(dx), static_cast<T*>(nullptr), nvec, C,     \
+                     bn_nt())
+  if (dtype == kF16) APPLY_ONLY(__half); else APPLY_ONLY(__hip_bfloat16);
+#undef APPLY_ONLY
 }
 
 void bn_nhwc_backward(int dtype, const void* x, const void* dy, const void* y, const uint8_t* mask, void* dx,
